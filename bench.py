@@ -14,10 +14,17 @@ backward and Adam; "shard" keeps the Gaussians sharded over the ranks and exchan
 rows with two all-to-alls per step (rodygs_amd/sharded.py); the default "both" times exactly K steps of each, back to
 back, prints the faster one as `value` (its name in config.parallelism) and both under `dp_modes`.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR also writes what the last timed step computed (step_outputs) as DIR/<name>.npy; such a run steps on the
+deterministic compositing backward (the same bits every run; config.deterministic_backward says so, and its ms_per_step is
+that path's, slower than the float-atomic one a plain run times).
+With --full the JSON line also carries
+  stage_ms     : per-stage milliseconds from a few extra steps after the timed region, and the per-stage rooflines;
   roofline     : the dominant kernel (render backward) -- ALGORITHMIC bytes per launch / its average duration,
                  measured live with hipEvents recorded by the library on the launch stream (DESIGN.md §5);
-  cpu_baseline : the PyTorch-CPU oracle timed on this box's host cores on a bounded sample of the same frame.
+  cpu_baseline : the PyTorch-CPU oracle timed on this box's host cores on a bounded sample of the same frame;
+  sub_records  : (the default workload only) the loop, reference-iteration, 100 k graph and PSNR-delta child runs,
+                 and the live rocprofv3 --pmc passes behind roofline.traffic.
 """
 import argparse
 import json
@@ -331,6 +338,24 @@ def cpu_baseline(frame, gt, hip, sh_degree, dev, budget_s=60.0, threads=16):
     return base, parity
 
 
+DUMP_ROWS = 65536        # --dump-outputs: rows of every per-Gaussian tensor written (a fixed, seeded sample of the cloud)
+
+
+def step_outputs(ds, loss, rows=DUMP_ROWS, seed=0):
+    """--dump-outputs: what a caller of DynamicScene.train_step holds after the last timed step -- the loss it returned and
+    the parameters its Adam update wrote: every per-Gaussian tensor on a fixed, seeded sample of `rows` rows (all rows of a
+    smaller cloud), the deformation MLP and the camera poses whole.  float32 host arrays, {file name: array}.
+    The inputs are seeded and a --dump-outputs run steps on the deterministic backward (run_mode): two runs write the same bits."""
+    with torch.no_grad():
+        sel = torch.randperm(ds.P, generator=torch.Generator().manual_seed(seed))[:rows].sort().values.to(ds.device)
+        out = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+        for k in ds.fp.names:
+            out["gaussians." + k] = ds.fp[k].detach()[sel].float().cpu().numpy()
+        for k in ds.sp.names:
+            out[("cameras." if k.startswith("cam_") else "mlp.") + k] = ds.sp[k].detach().float().cpu().numpy()
+    return out
+
+
 def capture_bench_frame(ds, frame_idx):
     """The rasterizer inputs the train step hands to the rasterizer for video frame `frame_idx`, as the parameters stand
     now (deformation MLP + per-Gaussian deformation + activations, that frame's learnable pose), copied to the host: what
@@ -363,6 +388,16 @@ def run_mode(args, mode, rank, world, dev, backend, scene, target):
         ds.track_densification()
     if args.no_normal:
         ds.raster_state.render_normal = False
+    if args.dump_outputs:
+        # every step of the run on the deterministic compositing backward (fixed-order reduction, no float atomics): the
+        # float-atomic default differs in the last bits from run to run and Adam's eps 1e-15 turns such a difference in a
+        # near-zero gradient into a whole lr step, so the outputs of the last timed step would depend on the run.  The same
+        # compositing kernel (rdg_render_bwd) runs either way; only its flush differs (per-instance rows + rdg_det_reduce
+        # instead of float atomics), and the eager pose-gradient branch stays on the launch stream.
+        ds.raster_state.deterministic = True
+        if rank == 0:
+            print("bench.py: --dump-outputs: every step runs on the deterministic compositing backward (RDG_DETERMINISTIC): "
+                  "ms_per_step is that path's, a plain run times the float-atomic one", file=sys.stderr)
     n_gt = min(args.gt_frames * world, args.frames)
     perm = sorted(set(int(round(i * args.frames / n_gt)) % args.frames for i in range(n_gt)))
     # Visit order: the reference draws its frames from a random permutation of the video (src/data/dataloader.py:28-71).  Its
@@ -453,10 +488,11 @@ def run_mode(args, mode, rank, world, dev, backend, scene, target):
         step = graphed.next_step
         train_step_eager = train_step
         train_step = lambda st_: graphed.step()                                  # noqa: E731
-    # Inside the timed region only the dominant kernel is bracketed by hipEvents (every timed stage costs ~10 us of
+    # --full: inside the timed region only the dominant kernel is bracketed by hipEvents (every timed stage costs ~10 us of
     # stream gap); the per-stage table is taken from a few extra steps afterwards.  (A replayed graph cannot bracket one
-    # of its kernels: the dominant kernel's time is then taken from the eager steps after the timed region.)
-    _lib.timing_enable(not use_graph, stages=["render_bwd"])
+    # of its kernels: the dominant kernel's time is then taken from the eager steps after the timed region.)  A plain run
+    # brackets nothing.
+    _lib.timing_enable(args.full and not use_graph, stages=["render_bwd"])
     _lib.timing_reset()
     deferred_in_timed_region = rstate.mode("deferred_overflow_check")
     sync()
@@ -466,12 +502,39 @@ def run_mode(args, mode, rank, world, dev, backend, scene, target):
         step += 1
     sync()
     dt = time.perf_counter() - t0
+    # what the last timed step computed, before any later step moves the parameters on
+    outputs = step_outputs(ds, loss) if args.dump_outputs and rank == 0 else None
     if graphed is not None:
         graphed.check()                      # raises if ANY replayed frame outgrew the captured capacity (sticky record)
         step = graphed.next_step
         graphed.close()
         train_step = train_step_eager
     rstate.poll_overflow(block=True)
+    if world > 1:
+        tt = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    out = {"mode": mode, "sharded": sharded, "dt": dt, "loss": float(loss.item()), "spatial_order": spatial_order,
+           "graph": graphed is not None, "densify_stats": densify_stats, "deferred": deferred_in_timed_region,
+           # the binning algorithm the timed steps ran: forced by RDG_BIN_MODE, or what the per-frame rule has picked
+           "radix": bool(rstate.mode("force_radix") or any(rstate.bin_hint.values())),
+           "deterministic": rstate.mode("deterministic"), "render_normal": rstate.mode("render_normal"),
+           "points_after_densify": points_after, "outputs": outputs}
+    if args.full:
+        out.update(_after_timed_region(args, rank, world, ds, ss, rstate, train_step, step, sync, sharded, perm, graphed))
+    rstate.deferred_overflow_check = None
+    del ds, ss, train_step
+    gc.unfreeze()
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def _after_timed_region(args, rank, world, ds, ss, rstate, train_step, step, sync, sharded, perm, graphed):
+    """--full: the per-stage table from a few extra steps (every stage bracketed), D, V and S of the frames the timed region
+    cycled through, and the bench frame the cpu_baseline leg and the parity check use."""
+    from rodygs_amd import _lib, rasterizer
+    H, W = args.height, args.width
     dom = _lib.stage_times()["render_bwd"]
     _lib.timing_enable(True)
     _lib.timing_reset()
@@ -488,17 +551,7 @@ def run_mode(args, mode, rank, world, dev, backend, scene, target):
         stages["render_bwd"] = dom           # the dominant kernel: per LAUNCH over the timed region (what `roofline` prices)
     _lib.timing_enable(False)
     rstate.deferred_overflow_check = None
-    if world > 1:
-        tt = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
-    out = {"mode": mode, "sharded": sharded, "dt": dt, "loss": float(loss.item()), "spatial_order": spatial_order,
-           "graph": graphed is not None, "densify_stats": densify_stats, "deferred": deferred_in_timed_region,
-           # the binning algorithm the timed steps ran: forced by RDG_BIN_MODE, or what the per-frame rule has picked
-           "radix": bool(rstate.mode("force_radix") or any(rstate.bin_hint.values())),
-           "deterministic": rstate.mode("deterministic"), "render_normal": rstate.mode("render_normal"),
-           "points_after_densify": points_after,
-           "per_stage": {k: (ms / n if n else 0.0) for k, (ms, n) in stages.items()}}
+    out = {"per_stage": {k: (ms / n if n else 0.0) for k, (ms, n) in stages.items()}}
     if rank == 0:
         if sharded:
             out["D"] = int(rstate.capacity_hint.get(ss.key, 0))
@@ -533,10 +586,6 @@ def run_mode(args, mode, rank, world, dev, backend, scene, target):
     if rank == 0 and world == 1 and not sharded and not args.no_cpu_baseline:
         # the frame the cpu_baseline leg times the oracle on and the parity check compares: first frame of the cycle
         out["bench_frame"] = capture_bench_frame(ds, perm[0])
-    del ds, ss, train_step
-    gc.unfreeze()
-    gc.collect()
-    torch.cuda.empty_cache()
     return out
 
 
@@ -809,6 +858,104 @@ def run_reference_iteration(args, dev):
                                                    "trainer steps and clears)", "densify_stats": True,
                        "deferred_overflow_check": True},
             "ms_per_sub_step": dt / args.steps * 1e3 / 2, "losses": [float(v) for v in loss]}
+
+
+def roofline_records(args, best, world, fps, sh_adam_in_backward, radix_binning):
+    """--full: the per-stage table, the step / stage rooflines and the dominant kernel's roofline of the run `best`, from the
+    extra steps and renders after its timed region (_after_timed_region).  Returns (records, config entries, the dominant
+    kernel's algorithmic bytes per launch)."""
+    P, W, H = args.points, args.width, args.height
+    sharded, per_stage = best["sharded"], best["per_stage"]
+    D, V, S = best["D"], best["V"], best["S"]
+    D_ref = best.get("D_ref", D)
+    P_eff = best["points_after_densify"] or P
+    # dominant kernel: render backward.  Algorithmic bytes per launch (DESIGN.md §5 / SURVEY.md §8d):
+    #   D*44 (sorted id + 40-B splat features) + H*W*40 (5 upstream-gradient channels, final_T, n_contrib, +pad
+    #   as in the survey formula) + V*40 (10 accumulated floats per visible Gaussian)
+    dom = "render_bwd"
+    dom_ms = per_stage[dom]
+    alg_bytes = D * 44 + H * W * 40 + V * 40
+    # HBM traffic of that kernel from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE and
+    # --pmc WRITE_SIZE in separate runs, gfx950 correction applied); only valid for the workload it was taken on
+    # and for the kernel source it was taken with (kernel_source_hash): a stale file gives null, not a wrong number
+    traffic, traffic_note = None, "no PMC file for this workload"
+    try:
+        pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
+        wl = pmc["workload"]
+        if (wl["points"], wl["width"], wl["height"], wl.get("scene", "uniform")) != (P, W, H, args.scene):
+            traffic_note = f"profiles/{PMC_FILE} was taken on another workload"
+        elif pmc.get("kernel_source_hash") != kernel_source_hash():
+            traffic_note = (f"profiles/{PMC_FILE} was taken with kernel sources {pmc.get('kernel_source_hash')}, "
+                            f"the build has {kernel_source_hash()}: re-run scripts/refresh_profiles.sh")
+        else:
+            traffic = pmc["kernels"]["rdg_render_bwd_kernel"]["hbm_bytes_corrected"]
+            traffic_note = (f"profiles/{PMC_FILE}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, "
+                            f"kernel sources {pmc['kernel_source_hash']}")
+    except Exception as e:
+        traffic, traffic_note = None, f"profiles/{PMC_FILE} unreadable: {e}"
+    achieved = alg_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    # SURVEY.md §8d: whole-step and per-stage algorithmic bytes for the algorithm that actually ran
+    # (stage_bytes), and the FP32-VALU fraction of the two compositing kernels
+    K = 16
+    sb = stage_bytes(P_eff, K, V, D, H, W, world=world, sharded=sharded, sh_adam_in_backward=sh_adam_in_backward,
+                     radix_binning=radix_binning, densify_stats=best["densify_stats"])
+    sms = dict(per_stage)
+    sms["binning"] = per_stage["scan_dup"] + per_stage["sort"] + per_stage["ranges"]
+    stage_roofline = {k: {"algorithmic_bytes": b, "ms": sms[k],
+                          "hbm_frac": (b / (sms[k] * 1e-3) / 1e9 / HBM_PEAK_GBPS) if sms[k] > 0 else None}
+                      for k, b in sb.items()}
+    b_step = sum(sb.values())
+    # VALU-issue roofline of the two compositing kernels (they are issue-bound, not HBM-bound): wave instructions
+    # per launch from the SQ counters (committed PMC pass, valid only for the kernel sources it was taken with) over
+    # the kernel's SIMD-cycles = cycles per VALU instruction and SIMD, to be read against the measured issue classes
+    valu = {"issue_classes_cycles_per_inst": VALU_ISSUE_CLASSES, "source": None}
+    try:
+        sq = json.load(open(os.path.join(ROOT, "profiles", SQ_FILE)))
+        meta = sq.get("_meta", {})
+        wl = meta.get("workload") or {}
+        if meta.get("kernel_source_hash") != kernel_source_hash():
+            valu["source"] = f"profiles/{SQ_FILE} is stale (kernel sources changed): no VALU-issue figure"
+        elif (wl.get("points"), wl.get("width"), wl.get("height"), wl.get("scene", "uniform")) != (P, W, H, args.scene):
+            valu["source"] = f"profiles/{SQ_FILE} was taken on another workload"
+        else:
+            valu["source"] = f"profiles/{SQ_FILE} (rocprofv3 --pmc SQ_INSTS_VALU ... pass of this command)"
+            for stage, prefix in (("render_fwd", "void rdg_render_fwd_kernel"), ("render_bwd", "void rdg_render_bwd_kernel")):
+                row = next((v for k_, v in sq.items() if k_.startswith(prefix)), None)
+                if row is None or per_stage[stage] <= 0:
+                    continue
+                # GRBM_GUI_ACTIVE counts per XCD (8 of them): the kernel's duration in shader-clock cycles
+                cycles = row["GRBM_GUI_ACTIVE"] / 8.0
+                cpi = cycles * N_SIMD / row["SQ_INSTS_VALU"]
+                valu[stage] = {"valu_wave_insts_per_launch": row["SQ_INSTS_VALU"],
+                               "salu_wave_insts_per_launch": row["SQ_INSTS_SALU"],
+                               "kernel_cycles": cycles, "cycles_per_valu_inst_per_simd": cpi,
+                               # every slot filled with the cheapest class would be 2.3: the fraction of the
+                               # issue-rate ceiling this kernel's instruction stream reaches
+                               "frac_of_issue_ceiling": VALU_ISSUE_CLASSES["f32 mul/add/fma/mov with VGPR sources"] / cpi}
+    except Exception as e:
+        valu["source"] = f"profiles/{SQ_FILE} unreadable: {e}"
+    return ({"stage_ms": per_stage,
+             "step_roofline": {"algorithmic_bytes_per_step": b_step, "achieved_GBps": b_step * fps / world / 1e9,
+                               "frac_of_8TBps": b_step * fps / world / 1e9 / HBM_PEAK_GBPS,
+                               "frac_of_6.3TBps_achievable": b_step * fps / world / 1e9 / 6300.0,
+                               "pixel_splat_pairs_S": S},
+             "stage_roofline": stage_roofline,
+             "render_valu_issue": valu,
+             "roofline": {"bound": "hbm", "kernel": "rdg_render_bwd_kernel", "achieved": achieved,
+                          "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                          "traffic": traffic, "traffic_source": traffic_note,
+                          "algorithmic_bytes_per_launch": alg_bytes, "avg_ms": dom_ms,
+                          "note": "the compositing kernels are VALU-issue bound (render_valu_issue); the HBM fraction is "
+                                  "reported because north_star asks for it",
+                          "second_roofline": {"bound": "valu_issue", **(valu.get("render_bwd") or {}),
+                                              "source": valu["source"]}}},
+            # D = (tile, Gaussian) instances of the REFERENCE algorithm's rectangles on these frames (what its key stream
+            # holds); D_composited = the instances this build bins, sorts and composites (tight rectangles,
+            # RdgRasterSettings.cull: the rest cannot blend in any pixel of their tile); num_rendered_D = the count the byte
+            # formulas above are evaluated with (= D_composited)
+            {"D": D_ref, "D_composited": D, "tight_tile_rectangles": best.get("cull", False), "num_rendered_D": D,
+             "visible_V": V},
+            alg_bytes)
 
 
 def launch_ranks(n, argv):
@@ -1095,8 +1242,20 @@ def main():
                          "'shard' = Gaussians sharded over the ranks, 64-byte splat records / gradient rows exchanged "
                          "with two all-to-alls (rodygs_amd/sharded.py); 'both' (default) times EXACTLY --steps steps of "
                          "each, back to back, reports the faster one as `value` and both under `dp_modes`")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: the per-stage table and rooflines (extra steps and "
+                         "renders after the timed region), the cpu_baseline leg with its parity check and, on the default "
+                         "workload, the sub-records and the live rocprofv3 --pmc passes; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1 step: after the timed steps write what the last one computed (bench.step_outputs: the loss "
+                         "and the updated parameters, per-Gaussian ones on a fixed sample of rows) as DIR/<name>.npy, float32; "
+                         "every step of such a run, timed ones included, uses the deterministic compositing backward "
+                         "(RDG_DETERMINISTIC), so two runs write the same bits; a plain run times the float-atomic backward")
     args = ap.parse_args()
 
+    if args.dump_outputs and (args.gpus != 1 or args.loop > 0 or args.iteration != "step" or os.environ.get("RDG_FORCE_SHARD")):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the single-GPU replicated step: not with --gpus N > 1, "
+                         "--loop, --iteration or RDG_FORCE_SHARD")
     if args.preflight:
         raise SystemExit(preflight(args.gpus))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1155,80 +1314,12 @@ def main():
 
     if rank == 0:
         best = min(runs, key=lambda r: r["dt"])
-        sharded, dt, per_stage = best["sharded"], best["dt"], best["per_stage"]
-        D, V, S, spatial_order = best["D"], best["V"], best["S"], best["spatial_order"]
-        D_ref = best.get("D_ref", D)
+        sharded, dt, spatial_order = best["sharded"], best["dt"], best["spatial_order"]
         graph_replay = best["graph"]
         fps = args.steps * world / dt
-        # dominant kernel: render backward.  Algorithmic bytes per launch (DESIGN.md §5 / SURVEY.md §8d):
-        #   D*44 (sorted id + 40-B splat features) + H*W*40 (5 upstream-gradient channels, final_T, n_contrib, +pad
-        #   as in the survey formula) + V*40 (10 accumulated floats per visible Gaussian)
-        dom = "render_bwd"
-        dom_ms = per_stage[dom]
-        alg_bytes = D * 44 + H * W * 40 + V * 40
-        # HBM traffic of that kernel from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE and
-        # --pmc WRITE_SIZE in separate runs, gfx950 correction applied); only valid for the workload it was taken on
-        # and for the kernel source it was taken with (kernel_source_hash): a stale file gives null, not a wrong number
-        traffic, traffic_note = None, "no PMC file for this workload"
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
-            wl = pmc["workload"]
-            if (wl["points"], wl["width"], wl["height"], wl.get("scene", "uniform")) != (P, W, H, args.scene):
-                traffic_note = f"profiles/{PMC_FILE} was taken on another workload"
-            elif pmc.get("kernel_source_hash") != kernel_source_hash():
-                traffic_note = (f"profiles/{PMC_FILE} was taken with kernel sources {pmc.get('kernel_source_hash')}, "
-                                f"the build has {kernel_source_hash()}: re-run scripts/refresh_profiles.sh")
-            else:
-                traffic = pmc["kernels"]["rdg_render_bwd_kernel"]["hbm_bytes_corrected"]
-                traffic_note = (f"profiles/{PMC_FILE}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, "
-                                f"kernel sources {pmc['kernel_source_hash']}")
-        except Exception as e:
-            traffic, traffic_note = None, f"profiles/{PMC_FILE} unreadable: {e}"
-        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # whole-step and per-stage algorithmic bytes for the algorithm that actually ran
-        # (stage_bytes), and the FP32-VALU fraction of the two compositing kernels
-        K = 16
         sh_adam_in_backward = bool(world == 1 and not sharded and not args.full_losses
                                    and os.environ.get("RDG_FUSE_SH_ADAM", "1") != "0")
         radix_binning = bool(best["radix"])
-        P_eff = best["points_after_densify"] or P
-        sb = stage_bytes(P_eff, K, V, D, H, W, world=world, sharded=sharded, sh_adam_in_backward=sh_adam_in_backward,
-                         radix_binning=radix_binning, densify_stats=best["densify_stats"])
-        sms = dict(per_stage)
-        sms["binning"] = per_stage["scan_dup"] + per_stage["sort"] + per_stage["ranges"]
-        stage_roofline = {k: {"algorithmic_bytes": b, "ms": sms[k],
-                              "hbm_frac": (b / (sms[k] * 1e-3) / 1e9 / HBM_PEAK_GBPS) if sms[k] > 0 else None}
-                          for k, b in sb.items()}
-        b_step = sum(sb.values())
-        # VALU-issue roofline of the two compositing kernels (they are issue-bound, not HBM-bound): wave instructions
-        # per launch from the SQ counters (committed PMC pass, valid only for the kernel sources it was taken with) over
-        # the kernel's SIMD-cycles = cycles per VALU instruction and SIMD, to be read against the measured issue classes
-        valu = {"issue_classes_cycles_per_inst": VALU_ISSUE_CLASSES, "source": None}
-        try:
-            sq = json.load(open(os.path.join(ROOT, "profiles", SQ_FILE)))
-            meta = sq.get("_meta", {})
-            wl = meta.get("workload") or {}
-            if meta.get("kernel_source_hash") != kernel_source_hash():
-                valu["source"] = f"profiles/{SQ_FILE} is stale (kernel sources changed): no VALU-issue figure"
-            elif (wl.get("points"), wl.get("width"), wl.get("height"), wl.get("scene", "uniform")) != (P, W, H, args.scene):
-                valu["source"] = f"profiles/{SQ_FILE} was taken on another workload"
-            else:
-                valu["source"] = f"profiles/{SQ_FILE} (rocprofv3 --pmc SQ_INSTS_VALU ... pass of this command)"
-                for stage, prefix in (("render_fwd", "void rdg_render_fwd_kernel"), ("render_bwd", "void rdg_render_bwd_kernel")):
-                    row = next((v for k_, v in sq.items() if k_.startswith(prefix)), None)
-                    if row is None or per_stage[stage] <= 0:
-                        continue
-                    # GRBM_GUI_ACTIVE counts per XCD (8 of them): the kernel's duration in shader-clock cycles
-                    cycles = row["GRBM_GUI_ACTIVE"] / 8.0
-                    cpi = cycles * N_SIMD / row["SQ_INSTS_VALU"]
-                    valu[stage] = {"valu_wave_insts_per_launch": row["SQ_INSTS_VALU"],
-                                   "salu_wave_insts_per_launch": row["SQ_INSTS_SALU"],
-                                   "kernel_cycles": cycles, "cycles_per_valu_inst_per_simd": cpi,
-                                   # every slot filled with the cheapest class would be 2.3: the fraction of the
-                                   # issue-rate ceiling this kernel's instruction stream reaches
-                                   "frac_of_issue_ceiling": VALU_ISSUE_CLASSES["f32 mul/add/fma/mov with VGPR sources"] / cpi}
-        except Exception as e:
-            valu["source"] = f"profiles/{SQ_FILE} unreadable: {e}"
         if world == 1:
             parallelism = "single GPU (frame-dp1)"
         elif sharded:
@@ -1257,12 +1348,6 @@ def main():
                        "points_after_densify": best["points_after_densify"],
                        "deterministic_backward": best["deterministic"], "render_normal": best["render_normal"],
                        "parallelism": parallelism,
-                       # D = (tile, Gaussian) instances of the REFERENCE algorithm's rectangles on these frames (what its key
-                       # stream holds); D_composited = the instances this build bins, sorts and composites (tight rectangles,
-                       # RdgRasterSettings.cull: the rest cannot blend in any pixel of their tile); num_rendered_D = the count the
-                       # byte formulas above are evaluated with (= D_composited)
-                       "D": D_ref, "D_composited": D, "tight_tile_rectangles": best.get("cull", False),
-                       "num_rendered_D": D, "visible_V": V,
                        "losses": "full (config 5 set)" if args.full_losses else "photometric",
                        # single-GPU photometric step: the per-Gaussian backward kernel applies the Adam update of the SH
                        # features itself (RDG_FUSE_SH_ADAM=0 restores the separate launch; same bits either way)
@@ -1271,22 +1356,11 @@ def main():
                        "row_order": "z-curve of the canonical positions" if spatial_order else "generator (random)"},
             "gaussians_per_s": fps * (best["points_after_densify"] or P),
             "loss": best["loss"],
-            "stage_ms": per_stage,
-            "step_roofline": {"algorithmic_bytes_per_step": b_step, "achieved_GBps": b_step * fps / world / 1e9,
-                              "frac_of_8TBps": b_step * fps / world / 1e9 / HBM_PEAK_GBPS,
-                              "frac_of_6.3TBps_achievable": b_step * fps / world / 1e9 / 6300.0,
-                              "pixel_splat_pairs_S": S},
-            "stage_roofline": stage_roofline,
-            "render_valu_issue": valu,
-            "roofline": {"bound": "hbm", "kernel": "rdg_render_bwd_kernel", "achieved": achieved,
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "traffic": traffic, "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_ms": dom_ms,
-                         "note": "the compositing kernels are VALU-issue bound (render_valu_issue); the HBM fraction is "
-                                 "reported because north_star asks for it",
-                         "second_roofline": {"bound": "valu_issue", **(valu.get("render_bwd") or {}),
-                                             "source": valu["source"]}},
         }
+        if args.full:
+            records, cfg, alg_bytes = roofline_records(args, best, world, fps, sh_adam_in_backward, radix_binning)
+            res["config"].update(cfg)
+            res.update(records)
         if world > 1:
             # every formulation that was timed (each EXACTLY --steps steps between barriers, max over ranks)
             res["dp_modes"] = {r["mode"] + ("" if r["sharded"] == (r["mode"] == "shard") else " (fell back to replicated)"):
@@ -1299,7 +1373,7 @@ def main():
                                              if dist.get_backend() == "nccl" else None),
                                     "devices_visible": torch.cuda.device_count(),
                                     "one_device": bool(os.environ.get("RDG_ONE_DEVICE"))}
-        if not args.no_cpu_baseline and world == 1:      # contract: the CPU leg runs at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # contract: the CPU leg runs at N = 1 only
             try:
                 if best.get("bench_frame") is not None:
                     frame, gt = best["bench_frame"]
@@ -1313,10 +1387,10 @@ def main():
                 res["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": torch.get_num_threads(),
                                        "host": {"cpu_count": n_cpu, "cpu_model": model},
                                        "kind": "port", "sample": f"failed: {type(e).__name__}: {e}"}
-        # the default headline run (BASELINE configs[2], N = 1, no mode flag) also carries the compact records of what DESIGN.md
-        # section 5 claims next to the step: the loop, the reference's iteration, the 100 k graph step, the PSNR delta -- child runs
-        # after everything above, outside every timed region of this process (its GPU memory is released first)
-        default_run = (world == 1 and (P, W, H, args.scene) == (1000000, 1920, 1080, "uniform") and not args.full_losses
+        # --full on the default headline workload (BASELINE configs[2], N = 1, no mode flag) also carries the compact records of
+        # what DESIGN.md section 5 claims next to the step: the loop, the reference's iteration, the 100 k graph step, the PSNR
+        # delta -- child runs after everything above, outside every timed region of this process (its GPU memory is released first)
+        default_run = (args.full and world == 1 and (P, W, H, args.scene) == (1000000, 1920, 1080, "uniform") and not args.full_losses
                        and not args.graph and not args.no_normal and not args.densify_first and not args.no_cpu_baseline
                        and not force_shard)
         if default_run and not args.no_sub_records:
@@ -1357,6 +1431,11 @@ def main():
                     res["roofline"]["second_roofline"] = {"bound": "valu_issue", **lv["render_bwd"], "source": note}
             else:
                 res["roofline"]["traffic_live_note"] = note
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in best["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     # The JSON line is the LAST line on stdout: RCCL writes its version banner through C stdio, which sits in a buffer until the
     # process exits when stdout is a pipe -- after Python's print.  Every rank flushes C stdio, the ranks meet, then rank 0 prints.
     import ctypes

@@ -2,7 +2,7 @@
 # A/B of library variants on the GPU box: one bench run per variant (and the regular build first), stage timers side by
 # side.   usage: scripts/ab.sh [bench args ...] -- <variant name> ...
 cd "$(dirname "$0")/.."
-ARGS=()
+ARGS=(--full)                  # the stage timers are part of the --full line
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS+=("$1"); shift; done
 shift
 mkdir -p gpurun_out/ab

@@ -6,6 +6,7 @@ REPS=$1; shift
 SETS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do SETS+=("$1"); shift; done
 [ "$1" == "--" ] && shift
+set -- --full "$@"              # the stage timers are part of the --full line
 mkdir -p gpurun_out/ab
 FILES=()
 for r in $(seq 1 $REPS); do

@@ -18,7 +18,7 @@ python3 scripts/pmc_hbm_traffic.py $O/pmc_fetch $O/pmc_write $O/${T}_pmc_hbm_tra
 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_LDS SQ_INSTS_SALU GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline > /dev/null 2> $O/pmc_sq.err
 python3 scripts/pmc_summary.py $O/pmc_sq $O/${T}_pmc_sq_counters.json 1000000 1920 1080 > /dev/null 2>&1
 cp $O/${T}_pmc_hbm_traffic.json $O/${T}_pmc_sq_counters.json $R/profiles/ 2>/dev/null
-python3 bench.py > $O/${T}_bench.json 2> $O/bench.err
+python3 bench.py --full > $O/${T}_bench.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${T}_bench_under_rocprof.json 2> $O/kt.err
 cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/${T}_bench_kernel_stats.csv
 python3 scripts/trace_one_step.py $O/kt > $O/${T}_one_step.txt 2>&1
@@ -46,34 +46,34 @@ python3 bench.py --iteration reference-v1 > $O/${T}_reference_iteration_v1_bench
 python3 bench.py --iteration reference-v1 --points 200000 > $O/${T}_reference_iteration_v1_200k_bench.json 2>/dev/null
 # the tight tile rectangles against the reference's (RdgRasterSettings.cull), alternating on this box
 for i in 1 2; do
-  RDG_CULL=1 python3 bench.py --steps 60 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=b['stage_ms']; print('cull 1', 'step %.4f ms' % b['ms_per_step'], 'D', b['config']['D'], 'D_composited', b['config']['D_composited'], 'binning %.1f us' % (1e3*(s['scan_dup']+s['sort']+s['ranges'])), 'render_fwd %.1f' % (1e3*s['render_fwd']), 'render_bwd %.1f' % (1e3*s['render_bwd']))"
-  RDG_CULL=0 python3 bench.py --steps 60 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=b['stage_ms']; print('cull 0', 'step %.4f ms' % b['ms_per_step'], 'D', b['config']['D'], 'D_composited', b['config']['D_composited'], 'binning %.1f us' % (1e3*(s['scan_dup']+s['sort']+s['ranges'])), 'render_fwd %.1f' % (1e3*s['render_fwd']), 'render_bwd %.1f' % (1e3*s['render_bwd']))"
+  RDG_CULL=1 python3 bench.py --full --steps 60 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=b['stage_ms']; print('cull 1', 'step %.4f ms' % b['ms_per_step'], 'D', b['config']['D'], 'D_composited', b['config']['D_composited'], 'binning %.1f us' % (1e3*(s['scan_dup']+s['sort']+s['ranges'])), 'render_fwd %.1f' % (1e3*s['render_fwd']), 'render_bwd %.1f' % (1e3*s['render_bwd']))"
+  RDG_CULL=0 python3 bench.py --full --steps 60 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=b['stage_ms']; print('cull 0', 'step %.4f ms' % b['ms_per_step'], 'D', b['config']['D'], 'D_composited', b['config']['D_composited'], 'binning %.1f us' % (1e3*(s['scan_dup']+s['sort']+s['ranges'])), 'render_fwd %.1f' % (1e3*s['render_fwd']), 'render_bwd %.1f' % (1e3*s['render_bwd']))"
 done > $O/${T}_cull_ab.txt
 # the randomised sweeps on seeds of their own (the -m gpu test runs 300 + 300 on 610000 / 620000 under frozen rules)
 python3 scripts/parity_sweep.py 1500 630000 > $O/${T}_parity_sweep_regular.txt 2>&1
 RDG_SWEEP_PROFILE=aniso python3 scripts/parity_sweep.py 1500 640000 > $O/${T}_parity_sweep_aniso.txt 2>&1
 # the two scenes the survey's generator never enters (not the headline): bench line + kernel table each
 for SC in sheets dense; do
-  python3 bench.py --scene $SC --no-cpu-baseline > $O/${T}_scene_${SC}_bench.json 2>/dev/null
+  python3 bench.py --full --scene $SC --no-cpu-baseline > $O/${T}_scene_${SC}_bench.json 2>/dev/null
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$SC -- python3 bench.py --scene $SC --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2> $O/kt_$SC.err
   cp $(find $O/kt_$SC -name "*kernel_stats.csv" | head -1) $O/${T}_scene_${SC}_kernel_stats.csv
   rm -rf $O/kt_$SC
 done
 # launch-bound regime (the reference's real clouds are ~100 k points): eager vs one captured graph per step
-python3 bench.py --points 100000 --no-cpu-baseline > $O/${T}_photometric_100k_bench.json 2>/dev/null
-python3 bench.py --points 100000 --no-cpu-baseline --graph > $O/${T}_photometric_100k_graph_bench.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --graph > $O/${T}_graph_bench.json 2>/dev/null
+python3 bench.py --full --points 100000 --no-cpu-baseline > $O/${T}_photometric_100k_bench.json 2>/dev/null
+python3 bench.py --full --points 100000 --no-cpu-baseline --graph > $O/${T}_photometric_100k_graph_bench.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --graph > $O/${T}_graph_bench.json 2>/dev/null
 # the config-5 loss set under the graph (four replayed steps between two eager rigidity steps), at the reference's real cloud size
-python3 bench.py --points 100000 --full-losses --no-cpu-baseline > $O/${T}_full_losses_100k_bench.json 2>/dev/null
-python3 bench.py --points 100000 --full-losses --no-cpu-baseline --graph > $O/${T}_full_losses_100k_graph_bench.json 2>/dev/null
+python3 bench.py --full --points 100000 --full-losses --no-cpu-baseline > $O/${T}_full_losses_100k_bench.json 2>/dev/null
+python3 bench.py --full --points 100000 --full-losses --no-cpu-baseline --graph > $O/${T}_full_losses_100k_graph_bench.json 2>/dev/null
 # the step on a cloud that went through one densify-and-prune (not a BASELINE config)
-python3 bench.py --no-cpu-baseline --densify-first > $O/${T}_densified_bench.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --densify-first > $O/${T}_densified_bench.json 2>/dev/null
 # the radix binning forced on the headline frame (the default picks bucket binning there)
-RDG_BIN_MODE=radix python3 bench.py --no-cpu-baseline > $O/${T}_radix_binning_bench.json 2>/dev/null
-python3 bench.py --points 4000000 --width 3840 --height 2160 --steps 10 --warmup 5 --gt-frames 4 --no-cpu-baseline > $O/${T}_photometric_4m_4k_bench.json 2>/dev/null
-python3 bench.py --full-losses --no-cpu-baseline > $O/${T}_full_losses_bench.json 2>/dev/null
-python3 bench.py --full-losses --points 4000000 --width 3840 --height 2160 --steps 10 --warmup 5 --gt-frames 4 --no-cpu-baseline > $O/${T}_full_losses_4m_4k_bench.json 2>/dev/null
-RDG_DETERMINISTIC=1 python3 bench.py --no-cpu-baseline > $O/${T}_deterministic_bench.json 2>/dev/null
+RDG_BIN_MODE=radix python3 bench.py --full --no-cpu-baseline > $O/${T}_radix_binning_bench.json 2>/dev/null
+python3 bench.py --full --points 4000000 --width 3840 --height 2160 --steps 10 --warmup 5 --gt-frames 4 --no-cpu-baseline > $O/${T}_photometric_4m_4k_bench.json 2>/dev/null
+python3 bench.py --full --full-losses --no-cpu-baseline > $O/${T}_full_losses_bench.json 2>/dev/null
+python3 bench.py --full --full-losses --points 4000000 --width 3840 --height 2160 --steps 10 --warmup 5 --gt-frames 4 --no-cpu-baseline > $O/${T}_full_losses_4m_4k_bench.json 2>/dev/null
+RDG_DETERMINISTIC=1 python3 bench.py --full --no-cpu-baseline > $O/${T}_deterministic_bench.json 2>/dev/null
 # kernel tables of the config-5 loss set (every 5th step is a rigidity step)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_fl -- python3 bench.py --full-losses --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2> $O/kt_fl.err
 cp $(find $O/kt_fl -name "*kernel_stats.csv" | head -1) $O/${T}_full_losses_kernel_stats.csv
@@ -84,7 +84,7 @@ rm -rf $O/kt_fl $O/kt_fl4
 {
   for SC in uniform sheets dense; do
     for M in bucket radix; do
-      RDG_BIN_MODE=$M python3 bench.py --scene $SC --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=b['stage_ms']; print('$SC', '$M', 'binning %.1f us' % (1e3*(s.get('scan_dup',0)+s.get('sort',0)+s.get('ranges',0))), 'step %.4f ms' % b['ms_per_step'])"
+      RDG_BIN_MODE=$M python3 bench.py --full --scene $SC --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=b['stage_ms']; print('$SC', '$M', 'binning %.1f us' % (1e3*(s.get('scan_dup',0)+s.get('sort',0)+s.get('ranges',0))), 'step %.4f ms' % b['ms_per_step'])"
     done
   done
 } > $O/${T}_binning_modes_raw.txt

@@ -7,7 +7,7 @@ if [ $# -eq 0 ]; then set -- "-DRDG_ABL_NOATOMIC" "-DRDG_ABL_NOATOMIC -DRDG_ABL_
 for v in "" "$@"; do
   rm -f rodygs_amd/csrc/rdg_render.o
   make -C rodygs_amd/csrc EXTRA="$v" > /dev/null 2>&1 || { echo "build failed: $v"; continue; }
-  python bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('variant [$v]', round(d['value'],1), {k:round(x,4) for k,x in d['stage_ms'].items() if 'render' in k})"
 done

@@ -3,12 +3,16 @@ import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# a step ends with rdg_adam_multi_kernel followed by torch small-Adam kernels; take the span between the last two adam launches
+# a step ends with its last rdg_adam_multi_kernel launch (a step launches it more than once: the rows' Adam next to the MLP
+# backward, then the MLP + pose bucket); the launches per step = adam launches / compositing-backward launches (one per step)
 idx = [i for i, r in enumerate(rows) if "rdg_adam_multi_kernel" in r["Kernel_Name"]]
-# bench.py: 5 warm-up steps, 20 timed steps (only the dominant kernel bracketed by events), 5 steps with every stage
-# bracketed (each bracket costs ~10 us of stream gap): show a step of the TIMED region unless told otherwise
-which = int(sys.argv[2]) if len(sys.argv) > 2 else (19 if len(idx) >= 26 else len(idx) - 2)
-a, b = idx[which], idx[which + 1]
+n_steps = sum("rdg_render_bwd_kernel" in r["Kernel_Name"] for r in rows)
+per = max(1, round(len(idx) / max(1, n_steps)))
+ends = idx[per - 1::per]
+# a plain bench.py run: the warm-up steps, the untimed settling steps, then the timed steps, all without events: by default
+# the LAST step, which is the last timed step (argv[2]: the index of another step, 1 = the second step of the trace)
+which = int(sys.argv[2]) if len(sys.argv) > 2 else len(ends) - 1
+a, b = ends[which - 1], ends[which]
 t0 = int(rows[a]["End_Timestamp"])
 prev_end = t0
 tot = 0

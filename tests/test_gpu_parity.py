@@ -2865,7 +2865,8 @@ def test_bench_runs_both_dp_formulations_the_way_the_driver_launches_it():
     env = dict(os.environ, RDG_ONE_DEVICE="1", RDG_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--points", "20000", "--width", "320", "--height", "240", "--frames", "8", "--gt-frames", "4"]
+           "--warmup", "1", "--points", "20000", "--width", "320", "--height", "240", "--frames", "8", "--gt-frames", "4",
+           "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -2908,6 +2909,38 @@ def test_plain_bench_command_with_gpus_2_launches_its_own_ranks():
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", *small], env=env, cwd=root,
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 2 and "needs 2 visible devices" in r.stderr and not r.stdout.strip()
+
+
+def test_bench_dump_outputs_are_the_same_bits_every_run(tmp_path):
+    """`bench.py --dump-outputs DIR` twice with the same arguments, each in a fresh process: the same files, the same bits
+    (the seeded inputs and the deterministic backward such a run steps on), float32, and the dumped loss is the `loss` of
+    the JSON line.  The outputs are those of the LAST timed step: one timed step more (--steps 5 against 4) changes every
+    parameter tensor the Adam update writes."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--gpus", "1", "--warmup", "2", "--settle", "3", "--points", "20000", "--width", "320", "--height", "240",
+             "--frames", "8", "--gt-frames", "4"]
+    lines = []
+    for run, steps in (("a", "4"), ("b", "4"), ("c", "5")):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *small, "--steps", steps,
+                            "--dump-outputs", str(tmp_path / run)], cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir()) and "loss.npy" in names and len(names) > 10
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), f"{n}: max |a - b| = {np.abs(a.astype(np.float64) - b).max()}"
+    assert lines[0]["config"]["deterministic_backward"] is True and lines[0]["steps"] == 4
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == np.float32(lines[0]["loss"]) and lines[0]["loss"] == lines[1]["loss"]
+    assert np.load(tmp_path / "a" / "gaussians.xyz.npy").shape == (20000, 3)          # a cloud below the sample size: every row
+    assert lines[2]["steps"] == 5 and sorted(p.name for p in (tmp_path / "c").iterdir()) == names
+    for n in names:
+        if n.startswith(("gaussians.", "mlp.")):
+            assert not np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "c" / n)), f"{n}: the fifth step changed nothing"
 
 
 def test_psnr_delta_through_the_real_train_step():
