@@ -355,6 +355,18 @@ __device__ __forceinline__ void rdg_wave_lds_sync() {
 // an LDS tile S[64][stride] (stride odd -> a lane walking its own row is bank-conflict free).  One lane per
 // Gaussian reading its own 48-float SH row straight from global memory touches 64 cache lines per load
 // instruction and uses 4-16 bytes of each; through here every global instruction moves 1 KB (or 256 B) contiguous.
+__device__ __forceinline__ void rdg_rows_to_lds_scalar(const float* __restrict__ g, long long first_row, long long n_rows,
+                                                       int row, int stride, float* S, int lane) {
+    const long long base = first_row * row, total = n_rows * row;
+    const float inv_row = 1.0f / (float)row;
+    for (int idx = lane; idx < 64 * row; idx += 64) {
+        const long long e = base + idx;
+        if (e < total) {
+            const int gi = (int)(((float)idx + 0.5f) * inv_row);
+            S[gi * stride + (idx - gi * row)] = g[e];
+        }
+    }
+}
 template <bool NT = true>
 __device__ __forceinline__ void rdg_rows_to_lds(const float* __restrict__ g, long long first_row, long long n_rows,
                                                 int row, int stride, float* S, int lane) {
@@ -386,12 +398,45 @@ __device__ __forceinline__ void rdg_rows_to_lds(const float* __restrict__ g, lon
             }
         }
     } else {
-        for (int idx = lane; idx < 64 * row; idx += 64) {
-            const long long e = base + idx;
-            if (e < total) {
-                const int gi = (int)(((float)idx + 0.5f) * inv_row);
-                S[gi * stride + (idx - gi * row)] = g[e];
-            }
+        rdg_rows_to_lds_scalar(g, first_row, n_rows, row, stride, S, lane);
+    }
+}
+// The same copy in two halves, for a caller that has other loads to issue in the same trip to memory: rdg_rows_issue
+// puts a lane's whole share of the tile in flight (row <= 48 floats: at most 12 loads of 16 B per lane, 768 per wave) and
+// stores nothing; rdg_rows_store writes the registers to the tile in the layout rdg_rows_to_lds leaves.  Only for rows of a
+// multiple of 4 floats at a 16-B aligned base (rdg_rows_vec4: then 16 * row is a multiple of 64 and `u < row / 4` is
+// uniform); a load past the end of the array is clamped to its last 16 bytes and its value is never stored.
+#define RDG_ROWS_MAXV 12
+typedef float rdg_row4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bool rdg_rows_vec4(const float* g, int row) {
+    return (row & 3) == 0 && row <= 4 * RDG_ROWS_MAXV && (((uintptr_t)g) & 15) == 0;
+}
+template <bool NT = true>
+__device__ __forceinline__ void rdg_rows_issue(const float* __restrict__ g, long long first_row, long long n_rows, int row,
+                                               int lane, rdg_row4 (&val)[RDG_ROWS_MAXV]) {
+    const long long base = first_row * row, total = n_rows * row;
+    const int nv = row >> 2;
+#pragma unroll
+    for (int u = 0; u < RDG_ROWS_MAXV; ++u) {
+        if (u < nv) {
+            const long long e = min(base + 4ll * (lane + 64 * u), total - 4);
+            val[u] = NT ? __builtin_nontemporal_load(reinterpret_cast<const rdg_row4*>(g + e))
+                        : *reinterpret_cast<const rdg_row4*>(g + e);
+        }
+    }
+}
+__device__ __forceinline__ void rdg_rows_store(long long first_row, long long n_rows, int row, int stride, float* S, int lane,
+                                               const rdg_row4 (&val)[RDG_ROWS_MAXV]) {
+    const long long base = first_row * row, total = n_rows * row;
+    const float inv_row = 1.0f / (float)row;
+    const int nv = row >> 2;
+#pragma unroll
+    for (int u = 0; u < RDG_ROWS_MAXV; ++u) {
+        const int v = lane + 64 * u;
+        if (u < nv && base + 4ll * v < total) {
+            const int gi = (int)(((float)(4 * v) + 0.5f) * inv_row);
+            float* dst = S + gi * stride + (4 * v - gi * row);
+            dst[0] = val[u].x; dst[1] = val[u].y; dst[2] = val[u].z; dst[3] = val[u].w;
         }
     }
 }

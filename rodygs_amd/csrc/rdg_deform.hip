@@ -192,25 +192,40 @@ rdg_deform_dcoeff16_kernel(int P, int Tu, const long long* __restrict__ time_ind
 // for its gradient on the way back); fused, a Gaussian's parameters are read once and its activated values written
 // once.  B = 16; the difference table sits in LDS exactly as in rdg_deform_dcoeff16_kernel.
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void rdg_diff16_to_lds(float* sm, int Tu, const float* __restrict__ bases) {
-    const float* bt = bases + (size_t)Tu * 112;          // packed bases: Tu table rows, then B(t)
-    // four elements per thread and trip, every load issued before the first LDS store: written as the plain loop the
-    // compiler waited for each pair of loads in turn (11 dependent L2 round trips at Tu = 100 before the kernel began)
+// One trip of the table build: four elements per thread, every load issued before the first LDS store (written as the
+// plain loop the compiler waited for each pair of loads in turn: 11 dependent L2 round trips at Tu = 100 before the kernel
+// began).  Packed bases: Tu table rows, then B(t).  The load half and the store half are separate so that a kernel can put
+// its own loads between them, into the same trip (rdg_dyn_getter_bwd_kernel).
+__device__ __forceinline__ void rdg_diff16_trip_load(int Tu, const float* __restrict__ bases, int k0, float (&a)[4],
+                                                     float (&b)[4]) {
+    const float* bt = bases + (size_t)Tu * 112;
     const int n = Tu * 112;
-    for (int k0 = threadIdx.x; k0 < n; k0 += 4 * blockDim.x) {
-        float a[4], b[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = min(k0 + q * (int)blockDim.x, n - 1);
-            const int u = k / 112, c = k - u * 112;
-            a[q] = bt[c]; b[q] = bases[(size_t)u * 112 + c];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = k0 + q * (int)blockDim.x;
-            if (k < n) { const int u = k / 112, c = k - u * 112; sm[u * RDG_DC_STRIDE + c] = a[q] - b[q]; }
-        }
+    for (int q = 0; q < 4; ++q) {
+        const int k = min(k0 + q * (int)blockDim.x, n - 1);
+        const int u = k / 112, c = k - u * 112;
+        a[q] = bt[c]; b[q] = bases[(size_t)u * 112 + c];
     }
+}
+__device__ __forceinline__ void rdg_diff16_trip_store(float* sm, int Tu, int k0, const float (&a)[4], const float (&b)[4]) {
+    const int n = Tu * 112;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int k = k0 + q * (int)blockDim.x;
+        if (k < n) { const int u = k / 112, c = k - u * 112; sm[u * RDG_DC_STRIDE + c] = a[q] - b[q]; }
+    }
+}
+// the trips from element k_first on (three trips in all at Tu = 100)
+__device__ __forceinline__ void rdg_diff16_rest_to_lds(float* sm, int Tu, const float* __restrict__ bases, int k_first) {
+    const int n = Tu * 112;
+    for (int k0 = k_first; k0 < n; k0 += 4 * blockDim.x) {
+        float a[4], b[4];
+        rdg_diff16_trip_load(Tu, bases, k0, a, b);
+        rdg_diff16_trip_store(sm, Tu, k0, a, b);
+    }
+}
+__device__ __forceinline__ void rdg_diff16_to_lds(float* sm, int Tu, const float* __restrict__ bases) {
+    rdg_diff16_rest_to_lds(sm, Tu, bases, threadIdx.x);
 }
 
 // The coefficient-gradient rows (64 B per Gaussian) leave the backward kernel through a wave-private LDS stage: written
@@ -295,8 +310,6 @@ rdg_dyn_getter_bwd_kernel(int P, int Tu, const long long* __restrict__ time_ind,
     extern __shared__ __attribute__((aligned(16))) float smem_dg[];
     // the finished-workgroup counter of the dB reduction's last stage is cleared here (one memset launch less)
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_zero; k += gridDim.x * blockDim.x) zero_out[k] = 0u;
-    rdg_diff16_to_lds(smem_dg, Tu, bases);
-    __syncthreads();
     // an absent upstream gradient reads the parameter of the same shape instead (any valid address) and is replaced by
     // zero afterwards: no branch between the loads, so all of a Gaussian's loads are in flight together (with the four
     // null tests as branches the loop made ten dependent round trips to memory per Gaussian: 2.7 TB/s)
@@ -306,24 +319,41 @@ rdg_dyn_getter_bwd_kernel(int P, int Tu, const long long* __restrict__ time_ind,
     const float4* pr = reinterpret_cast<const float4*>(has_r ? g_rots : rotation);
     const float* po = has_o ? g_opac : opacity;
     const int lane = threadIdx.x & 63;
+    const int step = gridDim.x * blockDim.x;
     float* stage = smem_dg + Tu * RDG_DC_STRIDE + (threadIdx.x >> 6) * (64 * RDG_DG_STAGE);
-    for (int p0 = (blockIdx.x * blockDim.x + threadIdx.x) - lane; p0 < P; p0 += gridDim.x * blockDim.x) {
-        const int p = p0 + lane;
-        const bool live = p < P;
-        const int pc = live ? p : P - 1;
-        const int u = (int)time_ind[pc];
-        const size_t sidx = (size_t)inv_order[pc];
-        float gm[3], gsc[3], sc[3];
+    int u; size_t sidx; float gm[3], gsc[3], sc[3]; float4 q, gr; float opv, gop;
+    auto load_row = [&](int pc) {
+        u = (int)time_ind[pc];
+        sidx = (size_t)inv_order[pc];
 #pragma unroll
         for (int k = 0; k < 3; ++k) { gm[k] = pm[3 * pc + k]; gsc[k] = ps[3 * pc + k]; sc[k] = scaling[3 * pc + k]; }
-        const float4 q = reinterpret_cast<const float4*>(rotation)[pc];
-        float4 gr = pr[pc];
-        const float opv = opacity[pc];
-        float gop = po[pc];
-        // loaded here, not behind a branch further down
+        q = reinterpret_cast<const float4*>(rotation)[pc];
+        gr = pr[pc];
+        opv = opacity[pc];
+        gop = po[pc];
+    };
+    // loaded here, not behind a branch further down
+    auto pin_row = [&]() {
         asm volatile("" : "+v"(sc[0]), "+v"(sc[1]), "+v"(sc[2]), "+v"(gr.x), "+v"(gr.y), "+v"(gr.z), "+v"(gr.w), "+v"(gop));
-        float qx = q.x, qy = q.y, qz = q.z, qw = q.w;
-        asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz), "+v"(qw));
+        asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+    };
+    // The loads of the wave's FIRST 64 Gaussians go out between the loads and the LDS stores of the table build's first trip
+    // (lanes past the end read the last row): one trip to memory less in front of the first result, 60.3 -> 50.7 us at
+    // P = 1 M.  Issued in front of the whole build they gain nothing: the build is a loop, and the wait at its head is for
+    // every load outstanding.  Later stretches load at the end of the iteration before, i.e. in the old order.  The forward
+    // kernel, with half as many loads per Gaussian, gained nothing measurable from the same change and keeps the plain form.
+    int p0 = (blockIdx.x * blockDim.x + threadIdx.x) - lane;
+    float ta[4], tb[4];
+    rdg_diff16_trip_load(Tu, bases, threadIdx.x, ta, tb);
+    load_row(min(p0 + lane, P - 1));
+    rdg_diff16_trip_store(smem_dg, Tu, threadIdx.x, ta, tb);
+    rdg_diff16_rest_to_lds(smem_dg, Tu, bases, threadIdx.x + 4 * blockDim.x);
+    __syncthreads();
+    pin_row();
+    for (; p0 < P; p0 += step) {
+        const int p = p0 + lane;
+        const bool live = p < P;
+        const float qx = q.x, qy = q.y, qz = q.z, qw = q.w;
 #pragma unroll
         for (int k = 0; k < 3; ++k) { gm[k] = has_m ? gm[k] : 0.0f; gsc[k] = has_s ? gsc[k] : 0.0f; }
         gr = has_r ? gr : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -390,6 +420,7 @@ rdg_dyn_getter_bwd_kernel(int P, int Tu, const long long* __restrict__ time_ind,
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) dc[q4] = make_float4(sacc[4 * q4], sacc[4 * q4 + 1], sacc[4 * q4 + 2], sacc[4 * q4 + 3]);
         rdg_stage_rows16_out(d_coeff, p0, P, stage, lane, dc);
+        if (p0 + step < P) { load_row(min(p0 + step + lane, P - 1)); pin_row(); }
     }
 }
 

@@ -110,11 +110,25 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
     // SH rows of the wave's 64 Gaussians: staged through LDS with wave-contiguous loads (rdg_rows_to_lds)
     __shared__ float sSH[RDG_PRE_BLOCK / 64][64 * 49];
     const int sh_row = d.M * 3, sh_stride = sh_row | 1;
+    const int lane = threadIdx.x & 63;
     const long long wave_first = (long long)bid * RDG_PRE_BLOCK + (threadIdx.x >> 6) * 64;
-    if (shs && wave_first < d.P) {
-        rdg_rows_to_lds(shs, wave_first, d.P, sh_row, sh_stride, sSH[threadIdx.x >> 6], threadIdx.x & 63);
+    // Rows of a multiple of 4 floats (SH degrees 1 and 3): the lane's whole share of the tile is put in flight here and
+    // stored to LDS only after the Gaussian's own loads have been issued too (below) -- ONE trip to memory per wave.  Staged
+    // by rdg_rows_to_lds (three dependent trips at 48 floats) with the geometry loaded behind it and opacity behind two
+    // branches, a wave made six dependent trips at 3 waves per SIMD: 4.9 TB/s.
+    const bool sh_stage = shs && wave_first < d.P, sh_vec = sh_stage && rdg_rows_vec4(shs, sh_row);
+    rdg_row4 shv[RDG_ROWS_MAXV];
+#pragma unroll
+    for (int u = 0; u < RDG_ROWS_MAXV; ++u) shv[u] = rdg_row4{0.f, 0.f, 0.f, 0.f};
+    if (sh_stage && !sh_vec) {
+        // rows of 3 and 27 floats (SH degrees 0 and 2) or an unaligned base: element by element, as before
+        rdg_rows_to_lds_scalar(shs, wave_first, d.P, sh_row, sh_stride, sSH[threadIdx.x >> 6], lane);
         rdg_wave_lds_sync();
     }
+    if (sh_vec) rdg_rows_issue(shs, wave_first, d.P, sh_row, lane, shv);
+    // lanes past the end load the last Gaussian's inputs (no branch around the loads) and store nothing
+    const bool live = i < d.P;
+    const int ic = live ? i : d.P - 1;
     // camera: uniform addresses -> scalar loads into SGPRs (the matrices live on the device because the
     // viewmatrix is the output of autograd-tracked pose math; no host round trip)
     __shared__ uint32_t wsum[RDG_PRE_BLOCK / RDG_WAVE];
@@ -133,14 +147,33 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
 #pragma unroll
     for (int k = 0; k < 16; ++k) { V[k] = view[k]; Pm[k] = proj[k]; }
     uint32_t my_tiles = 0;
-    if (i < d.P) {
+    // Every load of the Gaussian that the common path needs, before the first use and with no branch between them.  With a
+    // precomputed covariance there are no scales and rotations: the loads then read rows of the same shape that do exist
+    // (means3D; this camera's record rows) and the values are never used.
+    const float* __restrict__ sc_src = cov3Dp ? means3D : scales;
+    const float4* __restrict__ rot_src = cov3Dp ? reinterpret_cast<const float4*>(rec + ic) : reinterpret_cast<const float4*>(rots) + ic;
+    float x = means3D[3 * ic + 0], y = means3D[3 * ic + 1], z = means3D[3 * ic + 2];
+    float sc0 = sc_src[3 * ic + 0], sc1 = sc_src[3 * ic + 1], sc2 = sc_src[3 * ic + 2];
+    float4 q = *rot_src;
+    float op = opac[ic];
+    // pinned: issued here, in front of the first wait, together with the tile's loads (the first camera of the workgroup)
+    if (!MULTI || vw == 0) {
+#pragma unroll
+        for (int u = 0; u < RDG_ROWS_MAXV; ++u) asm volatile("" : "+v"(shv[u]));
+    }
+    asm volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(op), "+v"(sc0), "+v"(sc1), "+v"(sc2), "+v"(q.x), "+v"(q.y), "+v"(q.z),
+                 "+v"(q.w));
+    if ((!MULTI || vw == 0) && sh_vec) {
+        rdg_rows_store(wave_first, d.P, sh_row, sh_stride, sSH[threadIdx.x >> 6], lane, shv);
+        rdg_wave_lds_sync();
+    }
+    if (live) {
         int radius_out = 0;
         uint8_t cl = 0;
         uint4 rd = make_uint4(0u, 0u, 0u, 0u);
         RdgRec R;
         R.q0 = make_float4(0.f, 0.f, 0.f, 0.f);
         R.q1 = R.q0; R.q2 = R.q0; R.q3 = R.q0;
-        const float x = means3D[3 * i + 0], y = means3D[3 * i + 1], z = means3D[3 * i + 2];
         const float vx = ((V[0] * x + V[4] * y) + V[8] * z) + V[12];
         const float vy = ((V[1] * x + V[5] * y) + V[9] * z) + V[13];
         const float vz = ((V[2] * x + V[6] * y) + V[10] * z) + V[14];
@@ -158,9 +191,7 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
                 S00 = cov3Dp[6 * i + 0]; S01 = cov3Dp[6 * i + 1]; S02 = cov3Dp[6 * i + 2];
                 S11 = cov3Dp[6 * i + 3]; S12 = cov3Dp[6 * i + 4]; S22 = cov3Dp[6 * i + 5];
             } else {
-                const float s0 = d.smod * scales[3 * i + 0], s1 = d.smod * scales[3 * i + 1],
-                            s2 = d.smod * scales[3 * i + 2];
-                const float4 q = reinterpret_cast<const float4*>(rots)[i];
+                const float s0 = d.smod * sc0, s1 = d.smod * sc1, s2 = d.smod * sc2;
                 const float r = q.x, qx = q.y, qy = q.z, qz = q.w;
                 const float R00 = 1.0f - 2.0f * (qy * qy + qz * qz), R01 = 2.0f * (qx * qy - r * qz),
                             R02 = 2.0f * (qx * qz + r * qy);
@@ -179,7 +210,6 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
                 S22 = (L20 * L20 + L21 * L21) + L22 * L22;
                 if (d.render_normal) {
                     // shortest axis (first minimum) of R*diag(s), in view space, facing the camera
-                    const float sc0 = scales[3 * i + 0], sc1 = scales[3 * i + 1], sc2 = scales[3 * i + 2];
                     int k = 0; float sm = sc0;
                     if (sc1 < sm) { sm = sc1; k = 1; }
                     if (sc2 < sm) { sm = sc2; k = 2; }
@@ -224,7 +254,7 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
                 const float py = ((ndc_y + 1.0f) * (float)d.H - 1.0f) * 0.5f;
                 // record fields the rectangle is formed from (rdg_splat_rect reads nothing else)
                 const float4 rq0 = make_float4(px, py, cc * det_inv, -cb * det_inv);
-                const float4 rq1 = make_float4(ca * det_inv, opac[i], vz, __int_as_float(radius));
+                const float4 rq1 = make_float4(ca * det_inv, op, vz, __int_as_float(radius));
                 const float inv_cyy = 1.0f / cc;
                 int x0, y0, x1, y1;
                 rdg_rect(px, py, radius, d.gx, d.gy, x0, y0, x1, y1);
@@ -245,7 +275,7 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
                         float dx = x - camx, dy = y - camy, dz = z - camz;
                         const float ln = sqrtf((dx * dx + dy * dy) + dz * dz);
                         dx = dx / ln; dy = dy / ln; dz = dz / ln;
-                        const float* sh = sSH[threadIdx.x >> 6] + (threadIdx.x & 63) * sh_stride;
+                        const float* sh = sSH[threadIdx.x >> 6] + lane * sh_stride;
                         float res[3];
 #pragma unroll
                         for (int c = 0; c < 3; ++c) res[c] = SH_C0 * sh[c];
@@ -299,7 +329,7 @@ rdg_preprocess_fwd_kernel(RdgDev d, const float* __restrict__ view_b, const floa
     }
     // block sum of tiles_touched -> block_sums[bid]
     uint32_t inc = rdg_wave_scan_incl(my_tiles);
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t w = threadIdx.x >> 6;
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[bid] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
